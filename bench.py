@@ -16,7 +16,20 @@ the best of three solves from A in host memory through elp_load_dense, the
 entry point the R glue calls (`host_input.c3`); the HBM-resident time per
 solve is `time_to_optimal_hbm_s`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the W warm-up and the K timed solves, and prints the
+result line: the headline figures and what the timed solves' own statistics
+give (`final`, `roofline`, `iteration_roofline`).  `time_to_optimal_s` is then
+the HBM-resident time per solve (`time_to_optimal_source` says which).
+`--dump-outputs DIR` writes what the last timed solve returned to its caller
+(status, objective, x, duals, basis) as DIR/<name>.npy, float64; the LP is
+seeded, so two builds run with the same arguments solve the same LP.
+`--full` adds every other leg, each a run of its own: the steady-state window,
+the other pricing rule, the solves from host memory (`host_input`), the
+10000x500000 config, configs[1], the sparse and the reference-sized LPs, the
+CPU oracle and HiGHS legs and the committed HBM-traffic profile; the per-leg
+switches (--c4, --sparse, --window, --no-cpu, ...) select among them there.
 
 Rank 0 prints one JSON line.  With N > 1 the columns are sharded over N
 GPUs (strong scaling: `value` is the iteration rate of the one LP).  Default
@@ -52,6 +65,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10, help="timed full solves")
     ap.add_argument("--warmup", type=int, default=2, help="untimed full solves")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (status, objective, x, y, basis) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (window, other pricing rule, host input, C4, C2, sparse, "
+                         "small LPs, CPU baselines); the per-leg switches below select among them")
     ap.add_argument("--m", type=int, default=5000)
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--seed", type=int, default=1)
@@ -96,7 +114,22 @@ def parse():
                     help="also report the steady-state rate over iterations [100, 1100) of one solve")
     a = ap.parse_args()
     a.rule = 1 if a.pricing == "devex" else 0
+    if not a.full:  # a plain run: the timed solves and nothing beside them
+        a.window = a.compare_rules = a.host_input = a.host_c4 = a.c4 = a.sparse = a.small = a.c2 = a.highs = 0
+        a.no_cpu = True
     return a
+
+
+def dump_outputs(path, sol):
+    """--dump-outputs: what the last timed solve handed back (Problem.solution:
+    elp_get_solution after elp_solve), one float64 array per file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if sol is None:  # (--steps 0: nothing was computed)
+        return
+    arrays = {"status": [sol.status], "objective": [sol.objval], "x": sol.x, "y": sol.y, "basis": sol.basis}
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def relaunch_under_torchrun(args) -> int:
@@ -809,8 +842,11 @@ def main():
                 "last workgroup end) on the pricing dispatches of every 8th chunk of the timed solves; HIP events "
                 "bound to the same dispatches in avg_launch_us_events")
     last = stats[-1] if stats else p.stats()
+    sol = p.solution(recs[-1][0]) if recs else None  # what the last timed solve returns to its caller
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sol)
     final = {"status": recs[-1][0] if recs else None, "iterations_to_optimal": last["iterations"],
-             "objective": p.solution(recs[-1][0]).objval if recs else None,
+             "objective": sol.objval if recs else None,
              "bump_dim": last["bump_dim"], "y_rows": last["y_rows"], "refactors": last["refactors"],
              "gj_refactors": last["gj_refactors"], "max_inv_resid": last["max_inv_resid"],
              "load_s": sum(s["seconds_load"] for s in stats) / max(len(stats), 1),
@@ -834,7 +870,7 @@ def main():
                   "us_per_iteration": 1e6 * tw / max(wit, 1), "price_frac": wr["frac"],
                   "price_avg_launch_us": wr["avg_launch_us"]}
 
-    traffic, traffic_src = committed_traffic(args) if max(world, ctx.ngpu) == 1 else (None, None)
+    traffic, traffic_src = committed_traffic(args) if args.full and max(world, ctx.ngpu) == 1 else (None, None)
     highs = HighsLeg(args) if rank == 0 and max(world, ctx.ngpu) == 1 and args.highs and not args.no_cpu else None
 
     other = None  # the same LP to optimality under the other pricing rule
@@ -908,6 +944,7 @@ def main():
             "n_gpus": max(world, ctx.ngpu),
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": 1e3 * elapsed / max(args.steps, 1),
             "higher_is_better": True,
             "scaling": "strong",

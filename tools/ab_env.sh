@@ -4,7 +4,7 @@
 # Same report as tools/ab_libs.sh.
 set -u
 mkdir -p gpurun_out
-ARGS=${BENCH_ARGS:-"--steps 3 --warmup 1 --no-cpu --c4 0 --sparse 0 --compare-rules 0"}
+ARGS=${BENCH_ARGS:-"--full --steps 3 --warmup 1 --no-cpu --c4 0 --sparse 0 --compare-rules 0"}
 i=0
 for E in ${ENVS:--}; do
   i=$((i + 1))

@@ -8,7 +8,7 @@
 # arguments (default: C3 only, 3 timed solves).
 set -u
 mkdir -p gpurun_out
-ARGS=${BENCH_ARGS:-"--steps 3 --warmup 1 --no-cpu --c4 0 --sparse 0 --compare-rules 0"}
+ARGS=${BENCH_ARGS:-"--full --steps 3 --warmup 1 --no-cpu --c4 0 --sparse 0 --compare-rules 0"}
 for V in ${VARIANTS:-base}; do
   if [ $V = base ]; then L=easylp_amd/lib/libeasylp_hip.so; else L=easylp_amd/lib/libeasylp_hip_$V.so; fi
   ELP_LIB_PATH=$PWD/$L timeout -k 10 200 python bench.py $ARGS > gpurun_out/ab_$V.json 2>gpurun_out/ab_$V.err || { echo "fail $V"; tail gpurun_out/ab_$V.err; exit 1; }

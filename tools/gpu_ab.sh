@@ -16,7 +16,7 @@ TAG=${TAG:-ab}
 (while sleep 30; do date +%T >> "$O/hb_$TAG.txt"; done) &
 HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
-Q="--steps ${STEPS:-10} --warmup 2 --c4 0 --sparse 0 --no-cpu --compare-rules 0"
+Q="--full --steps ${STEPS:-10} --warmup 2 --c4 0 --sparse 0 --no-cpu --compare-rules 0"
 QH="$Q --host-input 0 --highs 0"
 setup() {  # spec -> DIR ARGS ENVS
   local spec=$1

@@ -15,7 +15,7 @@ if [ -n "${TESTS:-}" ]; then
   rc=$?; tail -3 gpurun_out/c4ab_tests.log; [ $rc -ne 0 ] && exit $rc
 fi
 cd /tmp && export TMPDIR=/tmp
-Q="--steps 0 --warmup 0 --c4 1 --sparse 0 --no-cpu --compare-rules 0 --window 0 --host-input 0 --host-c4 0"
+Q="--full --steps 0 --warmup 0 --c4 1 --sparse 0 --no-cpu --compare-rules 0 --window 0 --host-input 0 --host-c4 0"
 for v in ${VARIANTS:-base pre}; do
   if [ $v = base ]; then L="$R/easylp_amd/lib/libeasylp_hip.so"; else L="$R/easylp_amd/lib/libeasylp_hip_$v.so"; fi
   ELP_LIB_PATH=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c4_$v -o run -- python3 "$R/bench.py" $Q > "$R/gpurun_out/c4_$v.json" 2> "$R/gpurun_out/c4_$v.err" || { echo "c4 $v failed"; tail -5 "$R/gpurun_out/c4_$v.err"; exit 5; }

@@ -1,6 +1,6 @@
 #!/bin/bash
-# One GPU-box session: parity tests, smoke, the bench line exactly as the
-# driver runs it (`bench.py --gpus 1 --steps 20 --warmup 5`), then the
+# One GPU session: parity tests, smoke, the bench line with every secondary
+# leg (`bench.py --gpus 1 --steps 20 --warmup 5 --full`), then the
 # profiles committed under profiles/:
 #   * rocprofv3 --kernel-trace --stats of the same timed region (the same 25
 #     full solves, without the secondary configs: every solve is identical, so
@@ -37,7 +37,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smo
 cat "$OUT/smoke_$TAG.log"
 fi
 
-timeout -k 10 600 python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || { echo "bench failed rc=$?"; tail -20 "$OUT/bench_$TAG.err"; exit 4; }
+timeout -k 10 600 python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || { echo "bench failed rc=$?"; tail -20 "$OUT/bench_$TAG.err"; exit 4; }
 cat "$OUT/bench_$TAG.json"
 
 REG="--steps $STEPS --warmup $WARM --c4 0 --sparse 0 --no-cpu --compare-rules 0 --window 0 --host-input 0 --host-c4 0 --c2 0 --small 0"
@@ -47,7 +47,7 @@ cp "$(find "$TMP/kt" -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats_$T
 python3 "$ROOT/tools/window_stats.py" "$(find "$TMP/kt" -name '*kernel_trace.csv' | head -1)" "$OUT/prof_bench_$TAG.json" > "$OUT/window_stats_$TAG.json" && cat "$OUT/window_stats_$TAG.json"
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex k_price --output-format csv -d "$TMP/pmc" -o run -- python3 "$ROOT/bench.py" $REG > "$OUT/pmc_bench_$TAG.json" 2> "$OUT/pmc_bench_$TAG.err" || { echo "rocprof pmc failed rc=$?"; tail -20 "$OUT/pmc_bench_$TAG.err"; exit 6; }
 python3 "$ROOT/tools/pmc_traffic.py" "$(find "$TMP/pmc" -name '*counter_collection.csv' | head -1)" "$OUT/pmc_bench_$TAG.json" > "$OUT/pmc_traffic_$TAG.json" && cat "$OUT/pmc_traffic_$TAG.json"
-WIN="--steps 0 --warmup 0 --window 1 --c4 0 --sparse 0 --no-cpu --compare-rules 0 --host-input 0 --host-c4 0 --c2 0 --small 0"
+WIN="--full --steps 0 --warmup 0 --window 1 --c4 0 --sparse 0 --no-cpu --compare-rules 0 --host-input 0 --host-c4 0 --c2 0 --small 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$TMP/tl" -o run -- python3 "$ROOT/bench.py" $WIN > "$OUT/tl_bench_$TAG.json" 2>&1 || { echo "rocprof timeline failed"; exit 7; }
 python3 "$ROOT/tools/timeline.py" "$(find "$TMP/tl" -name '*kernel_trace.csv' | head -1)" 100 1000 > "$OUT/timeline_$TAG.txt" && cat "$OUT/timeline_$TAG.txt"
 # the sparse 20000 x 100000 LPs: probe times, then the per-kernel

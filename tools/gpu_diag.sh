@@ -14,7 +14,7 @@ ELP_LIB_PATH="$ROOT/easylp_amd/lib/libeasylp_hip_diag.so" ELP_STAMPS=1 timeout -
     > "$OUT/stamps_$TAG.json" 2> "$OUT/stamps_$TAG.err" || { echo "stamps run failed"; tail -5 "$OUT/stamps_$TAG.err"; exit 6; }
 grep -A2 "k_ratio stamps" "$OUT/stamps_$TAG.err"
 TMP=/tmp/elp_diag_$TAG
-WIN="--steps 0 --warmup 0 --window 1 --c4 0 --sparse 0 --no-cpu --compare-rules 0 --host-input 0 --host-c4 0"
+WIN="--full --steps 0 --warmup 0 --window 1 --c4 0 --sparse 0 --no-cpu --compare-rules 0 --host-input 0 --host-c4 0"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$TMP/tl" -o run -- python3 "$ROOT/bench.py" $WIN \
     > "$OUT/tl_$TAG.json" 2>&1 || { echo "rocprof timeline failed"; exit 7; }
