@@ -25,8 +25,8 @@ ELP_SIMPLEX_PRIMAL_PRIMAL, ELP_SIMPLEX_DUAL_PRIMAL = 5, 6
 # every entry point the header declares (checked by tests/test_abi.py)
 EXPORTS = (
     "elp_default_control", "elp_create", "elp_load_dense", "elp_load_dense_device", "elp_load_dense_device_multi",
-    "elp_load_generated", "elp_generate_dense", "elp_load_csc", "elp_set_int", "elp_solve", "elp_iterate", "elp_get_solution",
-    "elp_get_stats", "elp_sensitivity",
+    "elp_load_generated", "elp_generate_dense", "elp_load_csc", "elp_set_int", "elp_solve", "elp_solve_batch", "elp_iterate",
+    "elp_get_solution", "elp_get_stats", "elp_sensitivity",
     "elp_set_trace", "elp_get_trace", "elp_comm_unique_id", "elp_comm_init", "elp_comm_init_host", "elp_comm_enable_p2p",
     "elp_destroy", "elp_last_error", "elp_abi_version",
 )
@@ -176,6 +176,7 @@ def load(path: str | None = None):
     lib.elp_load_csc.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     lib.elp_set_int.argtypes = [vp, vp]
     lib.elp_solve.argtypes = [vp, P(i32)]
+    lib.elp_solve_batch.argtypes = [P(vp), i64, P(i32), P(i64)]
     lib.elp_iterate.argtypes = [vp, i64, P(i32)]
     lib.elp_get_solution.argtypes = [vp, P(dbl), vp, vp, vp]
     lib.elp_get_stats.argtypes = [vp, P(ElpStats)]
@@ -194,7 +195,7 @@ def load(path: str | None = None):
                  "elp_load_generated",
                  "elp_generate_dense",
                  "elp_load_csc", "elp_sensitivity", "elp_set_int",
-                 "elp_solve", "elp_iterate", "elp_get_solution", "elp_get_stats",
+                 "elp_solve", "elp_solve_batch", "elp_iterate", "elp_get_solution", "elp_get_stats",
                  "elp_set_trace", "elp_get_trace", "elp_comm_unique_id", "elp_comm_init",
                  "elp_comm_init_host", "elp_comm_enable_p2p"):
         getattr(lib, name).restype = ctypes.c_int

@@ -1947,6 +1947,9 @@ static int ensure_res_pin(elp_handle* h) {
 }
 static double* res_pin_x(elp_handle* h) { return reinterpret_cast<double*>(h->res_pin + RES_PIN_X); }
 
+static int resident_exit(elp_handle* h, const ResOut& o, const double* x, int32_t warm, int32_t* lp_status,
+                         double seconds);
+
 // One launch runs the loop to its end: optimal, infeasible, unbounded, a
 // limit, or the elp_iterate budget (phase changes and refactors inside).
 // Returns 1 when the pipeline must run instead (a plan still pending).
@@ -1979,11 +1982,20 @@ static int run_resident(elp_handle* h, size_t lds, int32_t* lp_status, double t_
                           h->st));  // (the record and x together: the pinned block's layout)
     HIPCHK(hipStreamSynchronize(h->st));
     std::memcpy(&o, h->res_pin, sizeof(ResOut));
-    h->res_x.assign(res_pin_x(h), res_pin_x(h) + h->n);
+    return resident_exit(h, o, res_pin_x(h), a.warm, lp_status, now_s() - t_loop0);
+}
+
+// A resident launch's results into the handle (hctl holds the control block as
+// the launch left it, o its exit record, x the structurals' values): stats,
+// phase, the status mapping.  seconds: this launch's share of seconds_loop.
+static int resident_exit(elp_handle* h, const ResOut& o, const double* x, int32_t warm, int32_t* lp_status,
+                         double seconds) {
+    DevCtl* c = h->hctl;
+    h->res_x.assign(x, x + h->n);
     h->res_fresh = true;
     h->stats.host_polls++;
     // (a warm start's refactor is not counted: reload_bounds_warm resets the count after it)
-    h->stats.refactors += std::max<int64_t>(0, o.refactors - (a.warm ? 1 : 0));
+    h->stats.refactors += std::max<int64_t>(0, o.refactors - (warm ? 1 : 0));
     h->res_warm = 0;
     h->stats.gj_refactors += o.gj_refactors;
     if (h->ctl.refactor_mode == 0 && o.emax_max > h->stats.max_inv_resid) h->stats.max_inv_resid = o.emax_max;
@@ -2005,7 +2017,7 @@ static int run_resident(elp_handle* h, size_t lds, int32_t* lp_status, double t_
                      (long long)o.stage3[4], (long long)o.stage3[5]);
     h->phase = o.phase;
     const int32_t s = c->status;
-    h->stats.seconds_loop += now_s() - t_loop0;
+    h->stats.seconds_loop += seconds;
     if (s == ST_STOP) {
         c->status = ST_RUN;
         *lp_status = ELP_SUBOPTIMAL;
@@ -2678,6 +2690,225 @@ extern "C" int elp_solve(elp_handle* h, int32_t* lp_status) {
     }
     h->stats.seconds_total += now_s() - t0;
     return rc;
+}
+
+// ---------------------------------------------------------------- batch
+// elp_solve_batch: the members the resident solver takes run as one launch of
+// k_resident_batch, one workgroup each.  Per device, kept for
+// the library's lifetime: the launch's stream, the item records (pinned +
+// device) and the results arena (device + pinned) -- per item
+// [DevCtl][ResOut][x: n], one copy back for the whole batch.
+namespace {
+struct BatchCache {
+    int dev = -1;
+    hipStream_t st = nullptr;
+    ResItem* h_items = nullptr;  // pinned
+    ResItem* d_items = nullptr;
+    size_t item_cap = 0;
+    char* h_arena = nullptr;  // pinned
+    char* d_arena = nullptr;
+    size_t arena_cap = 0;
+};
+std::mutex g_batch_mu;  // (held for the whole batched part: one batch at a time uses the cache)
+std::vector<BatchCache> g_batch;
+constexpr size_t BA_CTL = (sizeof(DevCtl) + 63) & ~(size_t)63;
+
+struct BatchMember {
+    int64_t idx;
+    size_t lds, off;  // off: the member's block in the arena
+};
+}  // namespace
+
+static int batch_reserve(BatchCache& bc, size_t items, size_t arena) {
+    if (!bc.st) HIPCHK(hipStreamCreateWithFlags(&bc.st, hipStreamNonBlocking));
+    if (items > bc.item_cap) {
+        const size_t cap = std::max(items, 2 * bc.item_cap);
+        if (bc.h_items) (void)hipHostFree(bc.h_items);
+        if (bc.d_items) (void)hipFree(bc.d_items);
+        bc.h_items = bc.d_items = nullptr;
+        bc.item_cap = 0;
+        HIPCHK(hipHostMalloc((void**)&bc.h_items, cap * sizeof(ResItem)));
+        HIPCHK(hipMalloc((void**)&bc.d_items, cap * sizeof(ResItem)));
+        bc.item_cap = cap;
+    }
+    if (arena > bc.arena_cap) {
+        const size_t cap = std::max(arena, 2 * bc.arena_cap);
+        if (bc.h_arena) (void)hipHostFree(bc.h_arena);
+        if (bc.d_arena) (void)hipFree(bc.d_arena);
+        bc.h_arena = bc.d_arena = nullptr;
+        bc.arena_cap = 0;
+        HIPCHK(hipHostMalloc((void**)&bc.h_arena, cap));
+        HIPCHK(hipMalloc((void**)&bc.d_arena, cap));
+        bc.arena_cap = cap;
+    }
+    return 0;
+}
+
+// run_loop's preamble and run_resident's checks for one member of a batch.
+// *take = 0: elp_solve must run it (a plan pending); the handle is as it was
+// but for a refreshed mirror.  Else its control block is on its way to the
+// device on the batch's stream bst.
+static int batch_prepare(elp_handle* h, hipStream_t bst, int* take) {
+    *take = 0;
+    DevCtl* c = h->hctl;
+    if (!h->res_fresh && !h->ctl_fresh) {
+        HIPCHK(hipMemcpyAsync(c, h->d.ctl, sizeof(DevCtl), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+        h->ctl_fresh = true;
+    }
+    if (c->plan_seq != c->applied_seq || c->copy_seq != c->plan_seq) return 0;
+    if (!h->timing_started) {
+        h->t_solve_start = now_s();
+        h->timing_started = true;
+    }
+    // (before the mirror changes: a growth reads the device's block back into it)
+    int rc = ensure_ar(h, h->m);
+    if (rc) return rc;
+    rc = ensure_k(h, std::min(h->m, h->n));
+    if (rc) return rc;
+    h->res_fresh = false;
+    h->ctl_fresh = false;
+    c->iter_stop = INT64_MAX;
+    if (c->status == ST_STOP) c->status = ST_RUN;
+    c->phase = h->phase;
+    // Ordering: the shared launch must follow whatever the member's own
+    // (non-blocking) stream still holds -- a load's tail, a bound reload.  A
+    // synchronise, not an event: the stream is idle in the common case, and the
+    // control block can then go on the batch's stream with nothing to wait for.
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipMemcpyAsync(h->d.ctl, c, sizeof(DevCtl), hipMemcpyHostToDevice, bst));
+    *take = 1;
+    return 0;
+}
+
+extern "C" int elp_solve_batch(elp_handle* const* hs, int64_t count, int32_t* lp_status, int64_t* batched) {
+    if (count < 0) return fail(ELP_E_ARG, "elp_solve_batch: negative count");
+    if (batched) *batched = 0;
+    if (count == 0) return 0;
+    if (!hs || !lp_status) return fail(ELP_E_ARG, "elp_solve_batch: NULL argument");
+    for (int64_t i = 0; i < count; ++i) {
+        const elp_handle* h = hs[i];
+        if (!h) return fail(ELP_E_ARG, "elp_solve_batch: member " + std::to_string(i) + " is NULL");
+        if (!(is_group(h) ? h->ranks[0]->loaded : h->loaded))
+            return fail(ELP_E_ARG, "elp_solve_batch: member " + std::to_string(i) + " has no problem loaded");
+    }
+    {
+        std::vector<const elp_handle*> seen(hs, hs + count);
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+            return fail(ELP_E_ARG, "elp_solve_batch: a handle appears twice");
+    }
+    const double t0 = now_s();
+    // the members elp_solve would hand to run_resident (a pending plan is seen in batch_prepare)
+    std::vector<BatchMember> mem;
+    std::vector<char> taken((size_t)count, 0);
+    int bdev = -1;
+    for (int64_t i = 0; i < count; ++i) {
+        elp_handle* h = hs[i];
+        if (is_group(h) || h->done || !h->is_int.empty()) continue;
+        const size_t lds = resident_fit(h);
+        if (!lds) continue;
+        if (bdev < 0) bdev = h->dev;
+        if (h->dev != bdev) continue;
+        mem.push_back({i, lds, 0});
+    }
+    std::unique_lock<std::mutex> lk(g_batch_mu, std::defer_lock);
+    BatchCache* bc = nullptr;
+    int rc = 0;
+    if (!mem.empty()) {
+        lk.lock();
+        for (BatchCache& b : g_batch)
+            if (b.dev == bdev) bc = &b;
+        if (!bc) {
+            g_batch.emplace_back();
+            bc = &g_batch.back();
+            bc->dev = bdev;
+        }
+        HIPCHK(hipSetDevice(bdev));
+        size_t arena = 0;
+        for (BatchMember& b : mem) {
+            b.off = arena;
+            arena += BA_CTL + RES_PIN_X + (((size_t)hs[b.idx]->n * sizeof(double) + 63) & ~(size_t)63);
+        }
+        rc = batch_reserve(*bc, mem.size(), arena);
+        if (rc) return rc;
+        size_t nb = 0, lds_max = 0;
+        for (const BatchMember& b : mem) {
+            elp_handle* h = hs[b.idx];
+            int take = 0;
+            rc = batch_prepare(h, bc->st, &take);
+            if (rc) break;
+            if (!take) continue;
+            taken[(size_t)b.idx] = 1;
+            ResItem& it = bc->h_items[nb];
+            it.d = h->d;
+            it.a = ResArgs{};
+            it.a.phase = h->phase;
+            it.a.price_rule = h->ctl.pricing;
+            it.a.refactor_mode = h->ctl.refactor_mode;
+            it.a.warm = h->res_warm;
+            char* blk = bc->d_arena + b.off;
+            it.a.ctl_out = reinterpret_cast<DevCtl*>(blk);
+            it.a.out = reinterpret_cast<ResOut*>(blk + BA_CTL);
+            it.a.xout = reinterpret_cast<double*>(blk + BA_CTL + RES_PIN_X);
+            lds_max = std::max(lds_max, b.lds);
+            ++nb;
+        }
+        if (rc) {  // (control blocks of earlier members may be in flight)
+            (void)hipStreamSynchronize(bc->st);
+            return rc;
+        }
+        if (nb) {
+            // the time limits last: what is left of each at the launch
+            size_t k = 0;
+            for (const BatchMember& b : mem) {
+                if (!taken[(size_t)b.idx]) continue;
+                const elp_handle* h = hs[b.idx];
+                ResArgs& a = bc->h_items[k++].a;
+                a.tick_budget = 0;
+                if (h->ctl.time_limit > 0) {
+                    const double left = h->ctl.time_limit - (now_s() - h->t_solve_start);
+                    a.tick_budget = std::max<int64_t>(1, (int64_t)(left * 1e8));
+                }
+            }
+            hipError_t e = hipMemcpyAsync(bc->d_items, bc->h_items, nb * sizeof(ResItem), hipMemcpyHostToDevice, bc->st);
+            if (e == hipSuccess) e = launch_resident_batch(bc->d_items, (int)nb, lds_max, bc->st);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(bc->h_arena, bc->d_arena, arena, hipMemcpyDeviceToHost, bc->st);
+            if (e != hipSuccess) {
+                (void)hipStreamSynchronize(bc->st);
+                return fail(ELP_E_HIP, std::string("elp_solve_batch: ") + hipGetErrorString(e));
+            }
+        }
+        if (batched) *batched = (int64_t)nb;
+    }
+    // every other member by elp_solve, in order, while the launch runs
+    int rc_rest = 0;
+    std::string err_rest;
+    for (int64_t i = 0; i < count && !rc_rest; ++i)
+        if (!taken[(size_t)i]) {
+            rc_rest = elp_solve(hs[i], &lp_status[i]);
+            if (rc_rest) err_rest = g_err;
+        }
+    if (bc) {
+        HIPCHK(hipSetDevice(bdev));
+        HIPCHK(hipStreamSynchronize(bc->st));
+        const double secs = now_s() - t0;  // (the shared call's wall time, for every batched member)
+        for (const BatchMember& b : mem) {
+            if (!taken[(size_t)b.idx]) continue;
+            elp_handle* h = hs[b.idx];
+            const char* blk = bc->h_arena + b.off;
+            std::memcpy(h->hctl, blk, sizeof(DevCtl));
+            ResOut o{};
+            std::memcpy(&o, blk + BA_CTL, sizeof(ResOut));
+            const int32_t warm = h->res_warm;
+            rc = resident_exit(h, o, reinterpret_cast<const double*>(blk + BA_CTL + RES_PIN_X), warm,
+                               &lp_status[b.idx], secs);
+            h->stats.seconds_total += secs;
+            if (rc) return rc;
+        }
+    }
+    return rc_rest ? fail(rc_rest, err_rest) : 0;
 }
 
 extern "C" int elp_iterate(elp_handle* h, int64_t iters, int32_t* lp_status) {

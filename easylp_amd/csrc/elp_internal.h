@@ -462,8 +462,17 @@ struct ResArgs {
     int64_t tick_budget;
     ResOut* out;
     double* xout;
+    DevCtl* ctl_out;  // when set: the control block as the launch leaves it, copied here too
 };
 size_t resident_lds_bytes(int m, int n);
 hipError_t launch_resident(const Dev& d, const ResArgs& a, size_t lds, hipStream_t st);
+// many LPs in one launch (elp_solve_batch): workgroup b runs items[b] (device
+// memory) exactly as launch_resident(items[b].d, items[b].a); lds: the maximum
+// of the members' resident_lds_bytes
+struct ResItem {
+    Dev d;
+    ResArgs a;
+};
+hipError_t launch_resident_batch(const ResItem* items, int count, size_t lds, hipStream_t st);
 
 }  // namespace elp

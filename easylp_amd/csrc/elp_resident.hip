@@ -42,6 +42,10 @@
 
 #include <math.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 namespace elp {
 namespace {
 
@@ -1384,7 +1388,13 @@ RDEV void r_gather(T* dst, int64_t cnt, F src) {
     }
 }
 
-__global__ void __launch_bounds__(RW) k_resident(Dev d, ResArgs a) {
+// One LP's whole solve by the calling wave (k_resident: the launch's only
+// workgroup; k_resident_batch: one workgroup per LP).  Everything it touches is
+// the LP's own: d's buffers, the workgroup's LDS (carved from d.m, d.n whatever
+// the launch allocated) and the per-workgroup r_stat / r_prof.
+// (BATCH: a.ctl_out is read; the single launch leaves the argument alone)
+template <bool BATCH>
+RDEV void r_solve(const Dev& d, const ResArgs& a) {
     extern __shared__ __attribute__((aligned(16))) char r_smem[];
     RS s;
     r_carve(s, r_smem, d.m, d.n);
@@ -1751,7 +1761,37 @@ __global__ void __launch_bounds__(RW) k_resident(Dev d, ResArgs a) {
         for (int i = 0; i < 8; ++i) a.out->stage[i] = ELP_RES_PROF ? (int64_t)(r_prof[i] + (i == 0 ? 0 : 0)) : 0;
         for (int i = 8; i < 16; ++i) a.out->stage2[i - 8] = ELP_RES_PROF ? (int64_t)r_prof[i] : 0;
         for (int i = 16; i < 24; ++i) a.out->stage3[i - 16] = ELP_RES_PROF ? (int64_t)r_prof[i] : 0;
+        if (BATCH && a.ctl_out) *a.ctl_out = *g;  // (the batch's arena: one copy back for every LP)
     }
+}
+
+__global__ void __launch_bounds__(RW) k_resident(Dev d, ResArgs a) { r_solve<false>(d, a); }
+
+// Workgroup b solves items[b]: independent LPs side by side, each the single
+// launch's arithmetic.  The record's address is uniform and nothing the kernel
+// writes is const, so its fields are scalar loads as the kernel arguments are.
+__global__ void __launch_bounds__(RW) k_resident_batch(const ResItem* __restrict__ items) {
+    const ResItem& it = items[blockIdx.x];
+    r_solve<true>(it.d, it.a);
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize as raised so far, per device and
+// kernel (which: 0 k_resident, 1 k_resident_batch)
+hipError_t r_raise_lds(const void* fn, int which, size_t lds) {
+    if (lds <= 65536) return hipSuccess;
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, size_t> raised;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& cur = raised[{dev, which}];
+    if (lds > cur) {
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        cur = lds;
+    }
+    return hipSuccess;
 }
 
 }  // namespace
@@ -1763,13 +1803,20 @@ size_t resident_lds_bytes(int m, int n) {
 }
 
 hipError_t launch_resident(const Dev& d, const ResArgs& a, size_t lds, hipStream_t st) {
-    static size_t attr = 0;
-    if (lds > 65536 && lds > attr) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr = lds;
-    }
+    const hipError_t e = r_raise_lds((const void*)k_resident, 0, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_resident, dim3(1), dim3(RW), lds, st, d, a);
+    return hipGetLastError();
+}
+
+// lds: the largest member's (every workgroup of a launch allocates the same):
+// above 80 KiB one LP per CU, 256 co-resident; a batch of small LPs with one
+// large member runs at the large one's occupancy
+hipError_t launch_resident_batch(const ResItem* items, int count, size_t lds, hipStream_t st) {
+    if (count < 1) return hipSuccess;
+    const hipError_t e = r_raise_lds((const void*)k_resident_batch, 1, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_resident_batch, dim3(count), dim3(RW), lds, st, items);
     return hipGetLastError();
 }
 

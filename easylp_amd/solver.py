@@ -300,3 +300,60 @@ def solve_dense(A, dirs, rhs, obj, lo=None, up=None, maximize=False, trace=0, se
         if sensitivity and st == 0:
             sol.sens = p.sensitivity()
         return sol
+
+
+def solve_batch(problems) -> tuple[list[int], int]:
+    """elp_solve_batch over loaded Problems: (statuses, batched).  The same
+    results as [p.solve() for p in problems]; the members the resident solver
+    takes (small LPs) share one launch, `batched` of them."""
+    problems = list(problems)
+    if not problems:
+        return [], 0
+    lib = problems[0]._lib
+    hs = (ctypes.c_void_p * len(problems))(*[p._h for p in problems])
+    st = (ctypes.c_int32 * len(problems))(*([-1] * len(problems)))
+    nb = ctypes.c_int64(0)
+    check(lib.elp_solve_batch(hs, len(problems), st, ctypes.byref(nb)), "elp_solve_batch")
+    return list(st), int(nb.value)
+
+
+_LP_KEYS = ("A", "dirs", "rhs", "obj", "lo", "up", "maximize", "trace", "sensitivity", "is_int")
+
+
+def solve_dense_batch(lps, **control) -> list[Solution]:
+    """solve_dense for many LPs with one elp_solve_batch.  Each lp is the
+    argument tuple of solve_dense (A, dirs, rhs, obj[, lo, up, maximize]) or a
+    dict of its arguments by name (trace, sensitivity, is_int and per-LP
+    control overrides included); **control applies to every LP.  The loads are
+    per LP; Solution.stats["batched"] tells whether the LP shared the launch."""
+    probs = []
+    args = []
+    try:
+        for lp in lps:
+            if isinstance(lp, dict):
+                kw = dict(lp)
+            else:
+                kw = dict(zip(_LP_KEYS, lp))
+            a = {k: kw.pop(k, None) for k in _LP_KEYS}
+            ctl = dict(control)
+            ctl.update(kw)  # (what is left: control fields of this LP)
+            p = Problem(len(a["rhs"]), len(a["obj"]), **ctl)
+            probs.append(p)
+            args.append(a)
+            if a["trace"]:
+                p.set_trace(a["trace"])
+            p.load_dense(a["A"], a["dirs"], a["rhs"], a["obj"], a["lo"], a["up"], bool(a["maximize"]))
+            if a["is_int"] is not None:
+                p.set_int(a["is_int"])
+        sts, _ = solve_batch(probs)
+        out = []
+        for p, a, st in zip(probs, args, sts):
+            sol = p.solution(st)
+            sol.stats["batched"] = int(sol.stats["resident"] == 1 and a["is_int"] is None)
+            if a["sensitivity"] and st == 0:
+                sol.sens = p.sensitivity()
+            out.append(sol)
+        return out
+    finally:
+        for p in probs:
+            p.close()

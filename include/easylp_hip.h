@@ -285,6 +285,26 @@ int elp_set_int(elp_handle* h, const int32_t* is_int);
 /* solve(prob)                                          R/class.R:276 */
 int elp_solve(elp_handle* h, int32_t* lp_status);
 
+/* Many models at once: the same, handle for handle and bit for bit, as
+ *     for (i = 0; i < count; i++) elp_solve(hs[i], &lp_status[i]);
+ * (status, pivot trace, basis, objective, x, duals, the device state later
+ * calls read, and every elp_stats field but the seconds_* timings) -- but
+ * every member the resident solver takes (elp_control.resident) runs in ONE
+ * launch, one workgroup per LP, with one synchronisation and one copy back
+ * for all of them: a single small LP leaves all but one of the chip's 256
+ * compute units idle.  Batched: a loaded LP with m <= 64 whose state fits
+ * in LDS, resident != 2, no integer columns, not solved yet (nor decided at
+ * load: lower > upper), no ngpu / elp_comm_init* handle, on the device of the
+ * first such member.  Every other member is solved by elp_solve inside the
+ * call, in order, while the launch runs; the order of hs changes no result.
+ * *batched (may be NULL): how many members shared the launch.  A batched
+ * member's seconds_loop / seconds_total grow by the whole call's wall time.
+ * ELP_E_ARG before anything runs: count < 0; hs or lp_status NULL with
+ * count > 0; a NULL or unloaded member; a handle given twice.  count = 0
+ * returns 0.  There is no batched elp_iterate: iteration budgets stay one
+ * handle at a time. */
+int elp_solve_batch(elp_handle* const* hs, int64_t count, int32_t* lp_status, int64_t* batched);
+
 /* Run at most `iters` more simplex iterations (bench steps); *lp_status is
  * ELP_SUBOPTIMAL while the solve is still in progress. */
 int elp_iterate(elp_handle* h, int64_t iters, int32_t* lp_status);
