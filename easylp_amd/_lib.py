@@ -26,7 +26,7 @@ ELP_SIMPLEX_PRIMAL_PRIMAL, ELP_SIMPLEX_DUAL_PRIMAL = 5, 6
 EXPORTS = (
     "elp_default_control", "elp_create", "elp_load_dense", "elp_load_dense_device", "elp_load_dense_device_multi",
     "elp_load_generated", "elp_generate_dense", "elp_load_csc", "elp_set_int", "elp_solve", "elp_solve_batch", "elp_iterate",
-    "elp_get_solution", "elp_get_stats", "elp_sensitivity",
+    "elp_get_solution", "elp_get_stats", "elp_get_mip_info", "elp_sensitivity",
     "elp_set_trace", "elp_get_trace", "elp_comm_unique_id", "elp_comm_init", "elp_comm_init_host", "elp_comm_enable_p2p",
     "elp_destroy", "elp_last_error", "elp_abi_version",
 )
@@ -111,6 +111,18 @@ class ElpStats(ctypes.Structure):
     ]
 
 
+class ElpMipInfo(ctypes.Structure):
+    _fields_ = [
+        ("nodes", ctypes.c_int64),
+        ("lp_iterations", ctypes.c_int64),
+        ("tree_launches", ctypes.c_int64),
+        ("tree_nodes", ctypes.c_int64),
+        ("handbacks", ctypes.c_int64),
+        ("max_open", ctypes.c_int64),
+        ("reserved", ctypes.c_int64 * 2),
+    ]
+
+
 class ElpError(RuntimeError):
     pass
 
@@ -180,6 +192,7 @@ def load(path: str | None = None):
     lib.elp_iterate.argtypes = [vp, i64, P(i32)]
     lib.elp_get_solution.argtypes = [vp, P(dbl), vp, vp, vp]
     lib.elp_get_stats.argtypes = [vp, P(ElpStats)]
+    lib.elp_get_mip_info.argtypes = [vp, P(ElpMipInfo)]
     lib.elp_sensitivity.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.elp_set_trace.argtypes = [vp, i64]
     lib.elp_get_trace.argtypes = [vp, vp, i64, P(i64)]
@@ -196,7 +209,7 @@ def load(path: str | None = None):
                  "elp_generate_dense",
                  "elp_load_csc", "elp_sensitivity", "elp_set_int",
                  "elp_solve", "elp_solve_batch", "elp_iterate", "elp_get_solution", "elp_get_stats",
-                 "elp_set_trace", "elp_get_trace", "elp_comm_unique_id", "elp_comm_init",
+                 "elp_get_mip_info", "elp_set_trace", "elp_get_trace", "elp_comm_unique_id", "elp_comm_init",
                  "elp_comm_init_host", "elp_comm_enable_p2p"):
         getattr(lib, name).restype = ctypes.c_int
     if lib.elp_abi_version() != ABI_VERSION:  # (struct layouts would disagree)

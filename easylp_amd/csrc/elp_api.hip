@@ -151,6 +151,13 @@ struct elp_handle {
     // transfer wrote it), so run_loop skips its refresh
     bool ctl_fresh = false;
     std::vector<double> mip_x;   // branch and bound: the incumbent (elp_get_solution)
+    // the resident tree (run_tree): its record in device memory and
+    // the pinned block of its exchanges, kept across loads and solves of the
+    // handle (and by its spare), grown on demand
+    char* tree_dev = nullptr;
+    char* tree_pin = nullptr;
+    size_t tree_dev_bytes = 0, tree_pin_bytes = 0;
+    elp_mip_info mip_info{};     // the last branch and bound (elp_get_mip_info)
 };
 
 // elp_control.simplex = 0 (include/easylp_hip.h): lp_solve's default,
@@ -299,6 +306,8 @@ struct Spare {
     ResOut* resout = nullptr;
     int64_t resx_n = 0;  // (resout holds the record and x: sized by n)
     char* respin = nullptr;
+    char *tree_dev = nullptr, *tree_pin = nullptr;  // (sized in bytes: any next problem may take them)
+    size_t tree_dev_bytes = 0, tree_pin_bytes = 0;
 };
 static std::mutex g_spare_mu;
 static std::vector<Spare> g_spares;
@@ -318,6 +327,8 @@ static void spare_free(Spare& sp) {
     if (sp.hctl) (void)hipHostFree(sp.hctl);
     if (sp.resout) (void)hipFree(sp.resout);
     if (sp.respin) (void)hipHostFree(sp.respin);
+    if (sp.tree_dev) (void)hipFree(sp.tree_dev);
+    if (sp.tree_pin) (void)hipHostFree(sp.tree_pin);
     if (sp.st) (void)hipStreamDestroy(sp.st);
 }
 
@@ -567,6 +578,10 @@ extern "C" int elp_create(elp_handle** out, int64_t m, int64_t n, const elp_cont
                 h->keep_A = sp.keep_A;
                 h->keep_A_bytes = sp.keep_A_bytes;
                 h->hctl = sp.hctl;
+                h->tree_dev = sp.tree_dev;
+                h->tree_pin = sp.tree_pin;
+                h->tree_dev_bytes = sp.tree_dev_bytes;
+                h->tree_pin_bytes = sp.tree_pin_bytes;
                 if (sp.resx_n == n) {  // (sized by n)
                     h->d_resout = sp.resout;
                     h->res_pin = sp.respin;
@@ -2547,6 +2562,218 @@ static int reload_bounds_warm(elp_handle* h, const std::vector<double>& lo, cons
 // tree was not fully explored (a limit, max_nodes, a failed node); no
 // incumbent -> the failed node's status (1 iteration cap, 5, 7), 1 at the node
 // limit, else 2 (lp_solve's SUBOPTIMAL / TIMEOUT / NUMFAILURE conventions).
+namespace {
+struct BnbNode { std::vector<double> lo, up; };
+// run_bnb's state: what the resident tree hands back to the host loop
+struct BnbState {
+    std::vector<BnbNode> stack;
+    double best = HUGE_VAL;
+    bool have = false, limit = false, unbounded = false;
+    int32_t failed = -1;  // status of the first node LP that did not finish (incomplete tree)
+    int64_t nodes = 0, iters = 0;
+    std::vector<double> best_x;
+    bool warm_ok = false;
+    int64_t max_open = 1;
+};
+static_assert(LPS_OPTIMAL == ELP_OPTIMAL && LPS_SUBOPTIMAL == ELP_SUBOPTIMAL && LPS_INFEASIBLE == ELP_INFEASIBLE &&
+                  LPS_UNBOUNDED == ELP_UNBOUNDED && LPS_NUMFAILURE == ELP_NUMFAILURE && LPS_TIMEOUT == ELP_TIMEOUT,
+              "elp_internal.h mirrors the public status codes");
+// a test hook read at every solve (never cached: a test sets it in-process)
+int64_t env_i64(const char* name, int64_t dflt) {
+    const char* e = std::getenv(name);
+    return e && *e ? std::atoll(e) : dflt;
+}
+constexpr size_t tree_al(size_t v) { return (v + 63) & ~(size_t)63; }
+}  // namespace
+
+// The resident tree (k_resident_tree): the search from S's root
+// runs inside launches of one wave -- node LPs, stack and incumbent on the
+// device -- and S receives the result.  *finished: the search is over;
+// otherwise S holds the stack, incumbent and counters at the point where the
+// host loop takes over (a node failed numerically, or the device stack is
+// full), or nothing ran here at all (the root is for load_common to decide, or
+// a plan of the pipeline is pending).
+static int run_tree(elp_handle* h, size_t lds, double t_bnb, BnbState& S, bool* finished) {
+    *finished = false;
+    const int64_t n = h->n;
+    const size_t un = (size_t)n;
+    const BnbNode root = S.stack[0];
+    for (size_t j = 0; j < un; ++j)
+        if (root.lo[j] > root.up[j]) return 0;
+    if (!(h->lo_h == root.lo && h->up_h == root.up)) {  // (rounded integer bounds: today's cold load)
+        h->bnb_iter_left = h->ctl.max_iter;
+        const int rc = reload_bounds(h, root.lo, root.up);
+        if (rc) return rc;
+        if (h->done) return 0;
+    }
+    // run_loop's preamble and run_resident's checks
+    DevCtl* c = h->hctl;
+    if (!h->res_fresh && !h->ctl_fresh) {
+        HIPCHK(hipMemcpyAsync(c, h->d.ctl, sizeof(DevCtl), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+        h->ctl_fresh = true;
+    }
+    if (c->plan_seq != c->applied_seq || c->copy_seq != c->plan_seq) return 0;
+    h->res_fresh = false;
+    h->ctl_fresh = false;
+    c->iter_stop = INT64_MAX;
+    if (c->status == ST_STOP) c->status = ST_RUN;
+    c->phase = h->phase;
+    int rc = push_ctl_fields(h);
+    if (rc) return rc;
+    h->t_solve_start = t_bnb;  // time_limit counts from the start of the tree
+    h->timing_started = true;
+    const double t_loop0 = now_s();
+    rc = ensure_ar(h, h->m);
+    if (rc) return rc;
+    rc = ensure_k(h, std::min(h->m, h->n));
+    if (rc) return rc;
+    // the record: [TreeHdr][ResOut][DevCtl][x: n][best_x: n] come back with every
+    // launch; [obj: n][scol: n][isint: n][stack: cap x (lo: n, up: n)] stay
+    const int64_t cap = std::max<int64_t>(2, env_i64("ELP_TREE_STACK", 256));
+    const size_t o_out = tree_al(sizeof(TreeHdr)), o_ctl = o_out + RES_PIN_X, o_x = o_ctl + tree_al(sizeof(DevCtl));
+    const size_t o_bx = o_x + un * sizeof(double), back = o_bx + un * sizeof(double);
+    const size_t o_obj = tree_al(back), o_scol = o_obj + un * sizeof(double);
+    const size_t o_int = o_scol + tree_al(un * sizeof(int32_t)), o_stack = o_int + tree_al(un * sizeof(int32_t));
+    const size_t image = o_stack + 2 * un * sizeof(double);  // (with the root: what the host sends)
+    const size_t total = o_stack + (size_t)cap * 2 * un * sizeof(double);
+    if (h->tree_dev_bytes < total) {
+        if (h->tree_dev) (void)hipFree(h->tree_dev);
+        h->tree_dev = nullptr;
+        h->tree_dev_bytes = 0;
+        HIPCHK(hipMalloc((void**)&h->tree_dev, total));
+        h->tree_dev_bytes = total;
+    }
+    if (h->tree_pin_bytes < image) {
+        if (h->tree_pin) (void)hipHostFree(h->tree_pin);
+        h->tree_pin = nullptr;
+        h->tree_pin_bytes = 0;
+        HIPCHK(hipHostMalloc((void**)&h->tree_pin, image));
+        h->tree_pin_bytes = image;
+    }
+    char* pin = h->tree_pin;
+    std::memset(pin, 0, o_obj);
+    TreeHdr hd{};
+    hd.cap = (int32_t)cap;
+    hd.sp = 1;
+    hd.failed = -1;
+    hd.max_open = 1;
+    hd.max_nodes = h->ctl.max_nodes;
+    hd.max_iter = h->ctl.max_iter;
+    hd.slice_nodes = env_i64("ELP_TREE_SLICE_NODES", 0);
+    hd.slice_ticks = 2000000;  // 20 ms of the 100 MHz clock
+    hd.best = HUGE_VAL;
+    std::memcpy(pin, &hd, sizeof(hd));
+    std::memcpy(pin + o_obj, h->obj_h.data(), un * sizeof(double));
+    int32_t* scol = reinterpret_cast<int32_t*>(pin + o_scol);
+    for (size_t j = 0; j < un; ++j) scol[j] = h->scol_h.empty() ? 0 : h->scol_h[j];
+    std::memcpy(pin + o_int, h->is_int.data(), un * sizeof(int32_t));
+    std::memcpy(pin + o_stack, root.lo.data(), un * sizeof(double));
+    std::memcpy(pin + o_stack + un * sizeof(double), root.up.data(), un * sizeof(double));
+    HIPCHK(hipMemcpyAsync(h->tree_dev, pin, image, hipMemcpyHostToDevice, h->st));
+    char* dev = h->tree_dev;
+    TreeArgs t{};
+    t.hdr = reinterpret_cast<TreeHdr*>(dev);
+    t.best_x = reinterpret_cast<double*>(dev + o_bx);
+    t.obj = reinterpret_cast<const double*>(dev + o_obj);
+    t.scol = reinterpret_cast<const int32_t*>(dev + o_scol);
+    t.isint = reinterpret_cast<const int32_t*>(dev + o_int);
+    t.stack = reinterpret_cast<double*>(dev + o_stack);
+    ResArgs a{};
+    a.phase = h->phase;
+    a.price_rule = h->ctl.pricing;
+    a.refactor_mode = h->ctl.refactor_mode;
+    a.out = reinterpret_cast<ResOut*>(dev + o_out);
+    a.ctl_out = reinterpret_cast<DevCtl*>(dev + o_ctl);
+    a.xout = reinterpret_cast<double*>(dev + o_x);
+    int64_t launches = 0, ticks = 0;
+    for (;;) {
+        a.tick_budget = 0;
+        if (h->ctl.time_limit > 0) {  // (what is left since the tree started, as run_resident)
+            const double left = h->ctl.time_limit - (now_s() - t_bnb);
+            a.tick_budget = std::max<int64_t>(1, (int64_t)(left * 1e8));
+        }
+        HIPCHK(launch_resident_tree(h->d, a, t, lds, h->st));
+        HIPCHK(hipMemcpyAsync(pin, dev, back, hipMemcpyDeviceToHost, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+        std::memcpy(&hd, pin, sizeof(hd));
+        launches++;
+        ticks += reinterpret_cast<const ResOut*>(pin + o_out)->ticks;
+        if (hd.reason != TR_PAUSE) break;
+    }
+    S.best = hd.best;
+    S.have = hd.have != 0;
+    S.limit = hd.limit != 0;
+    S.unbounded = hd.unbounded != 0;
+    S.failed = hd.failed;
+    S.nodes = hd.nodes;
+    S.iters = hd.iters;
+    S.max_open = hd.max_open;
+    S.warm_ok = hd.reason != TR_NODE_FAILED;
+    if (S.have) {
+        const double* bx = reinterpret_cast<const double*>(pin + o_bx);
+        S.best_x.assign(bx, bx + n);
+    }
+    h->mip_info.tree_launches = launches;
+    h->mip_info.tree_nodes = hd.nodes;
+    const double* xs = reinterpret_cast<const double*>(pin + o_x);
+    if (hd.nodes > 0) {
+        // the handle as the per-node path leaves it after the node solved last
+        std::memcpy(c, pin + o_ctl, sizeof(DevCtl));
+        h->mb_epoch = c->mb_epoch;
+        if (hd.warm_last) {  // (reload_bounds_warm's reset)
+            h->stats = elp_stats{};
+            h->stats.world_size = h->comm.world;
+            h->stats.ncols = h->nloc;
+            h->stats.basis = ELP_BASIS_INVERSE;
+            h->dual_used = true;
+        }
+        ResOut o{};
+        std::memcpy(&o, pin + o_out, sizeof(ResOut));
+        o.ticks = ticks;
+        int32_t s = 0;
+        rc = resident_exit(h, o, xs, hd.warm_last, &s, now_s() - t_loop0);
+        if (rc) return rc;
+        h->stats.resident_launches = launches;
+    }
+    if (hd.reason == TR_END) {
+        *finished = true;
+        return 0;
+    }
+    // hand-back: the open nodes, and for a full stack the node whose children did
+    // not fit -- branched here on the x the launch brought back
+    h->mip_info.handbacks++;
+    const size_t cnt = (size_t)hd.sp + (hd.reason == TR_STACK_FULL ? 1 : 0);
+    std::vector<double> st(cnt * 2 * un);
+    if (cnt) {
+        HIPCHK(hipMemcpyAsync(st.data(), dev + o_stack, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+    }
+    S.stack.clear();
+    for (size_t k = 0; k < cnt; ++k) {
+        const double* p = st.data() + k * 2 * un;
+        S.stack.push_back({std::vector<double>(p, p + un), std::vector<double>(p + un, p + 2 * un)});
+    }
+    if (hd.reason == TR_STACK_FULL) {
+        BnbNode nd = std::move(S.stack.back());
+        S.stack.pop_back();
+        int64_t jb = -1;
+        double xb = 0.0;
+        for (int64_t j = 0; j < n && jb < 0; ++j) {
+            xb = unscale_col(h, xs[j], j, 1);
+            if (h->is_int[j] && std::fabs(xb - std::nearbyint(xb)) > 1e-7) jb = j;
+        }
+        if (jb < 0) return fail(ELP_E_STATE, "internal: a full tree stack without a branching column");
+        BnbNode fl = nd;  // floor child pushed first: the ceiling child is explored first
+        fl.up[jb] = std::floor(xb);
+        nd.lo[jb] = std::ceil(xb);
+        S.stack.push_back(std::move(fl));
+        S.stack.push_back(std::move(nd));
+        S.max_open = std::max<int64_t>(S.max_open, (int64_t)S.stack.size());
+    }
+    return 0;
+}
+
 static int run_bnb(elp_handle* h, int32_t* out_status) {
     const int64_t n = h->n;
     const double INF = HUGE_VAL, BIG = h->ctl.infinity;
@@ -2560,20 +2787,30 @@ static int run_bnb(elp_handle* h, int32_t* out_status) {
             if (u0[j] < INF) u0[j] = std::floor(u0[j] + 1e-9);
         }
     }
-    struct Node { std::vector<double> lo, up; };
-    std::vector<Node> stack;
+    using Node = BnbNode;
+    BnbState S;
+    std::vector<Node>& stack = S.stack;
     stack.push_back({l0, u0});
-    double best = INF;
+    double& best = S.best;
     Node best_node;
-    bool have = false, limit = false, unbounded = false;
-    int32_t failed = -1;  // status of the first node LP that did not finish (incomplete tree)
-    int64_t nodes = 0, iters = 0;
-    std::vector<double> x((size_t)n), best_x;
+    bool &have = S.have, &limit = S.limit, &unbounded = S.unbounded;
+    int32_t& failed = S.failed;
+    int64_t &nodes = S.nodes, &iters = S.iters;
+    std::vector<double> x((size_t)n);
+    std::vector<double>& best_x = S.best_x;
     // SIMPLEX_DUAL_PRIMAL on one GPU: node LPs after the first continue from
     // the basis of the node solved last (reload_bounds_warm; oracle warm_core)
     const bool warm = dual_phase1(h) && h->m > 0;
-    bool warm_ok = false;
-    while (!stack.empty()) {
+    bool& warm_ok = S.warm_ok;
+    h->mip_info = elp_mip_info{};
+    // a small MIP's whole tree inside resident launches (run_tree); what it
+    // hands back, if anything, the loop below finishes node by node
+    bool tree_finished = false;
+    if (const size_t lds = warm && env_i64("ELP_RESIDENT_TREE", 1) != 0 ? resident_fit(h) : 0) {
+        const int rc = run_tree(h, lds, t_bnb, S, &tree_finished);
+        if (rc) return rc;
+    }
+    while (!tree_finished && !stack.empty()) {
         Node nd = std::move(stack.back());
         stack.pop_back();
         if (h->ctl.max_nodes > 0 && nodes >= h->ctl.max_nodes) {
@@ -2650,6 +2887,7 @@ static int run_bnb(elp_handle* h, int32_t* out_status) {
         nd.lo[jb] = std::ceil(x[jb]);
         stack.push_back(std::move(fl));
         stack.push_back(std::move(nd));
+        S.max_open = std::max<int64_t>(S.max_open, (int64_t)stack.size());
     }
     int32_t status;
     if (unbounded) status = ELP_UNBOUNDED;
@@ -2666,6 +2904,9 @@ static int run_bnb(elp_handle* h, int32_t* out_status) {
     h->mip = true;
     h->mip_nodes = nodes;
     h->mip_iters = iters;
+    h->mip_info.nodes = nodes;
+    h->mip_info.lp_iterations = iters;
+    h->mip_info.max_open = S.max_open;
     *out_status = status;
     return 0;
 }
@@ -3315,6 +3556,14 @@ extern "C" int elp_get_stats(elp_handle* h, elp_stats* st) {
     return 0;
 }
 
+extern "C" int elp_get_mip_info(elp_handle* h, elp_mip_info* info) {
+    if (is_group(h)) return elp_get_mip_info(h->ranks[0], info);
+    if (!h || !info) return fail(ELP_E_ARG, "elp_get_mip_info: NULL argument");
+    if (!h->loaded || !h->mip) return fail(ELP_E_STATE, "elp_get_mip_info: the last solve was no MIP");
+    *info = h->mip_info;
+    return 0;
+}
+
 extern "C" int elp_set_trace(elp_handle* h, int64_t capacity) {
     if (is_group(h) && capacity >= 0)
         return fan_out(h, [&](elp_handle* r, int) { return elp_set_trace(r, capacity); }, false);
@@ -3406,6 +3655,12 @@ extern "C" void elp_destroy(elp_handle* h) {
         sp.resout = h->d_resout;
         sp.resx_n = h->n;
         sp.respin = h->res_pin;
+        sp.tree_dev = h->tree_dev;
+        sp.tree_pin = h->tree_pin;
+        sp.tree_dev_bytes = h->tree_dev_bytes;
+        sp.tree_pin_bytes = h->tree_pin_bytes;
+        sp.bytes += sp.tree_dev_bytes;
+        h->tree_dev = h->tree_pin = nullptr;
         h->pool.clear();
         h->keep_A = nullptr;
         h->hctl = nullptr;
@@ -3436,6 +3691,8 @@ extern "C" void elp_destroy(elp_handle* h) {
     release_kept(h);
     if (h->d_resout) (void)hipFree(h->d_resout);
     if (h->res_pin) (void)hipHostFree(h->res_pin);
+    if (h->tree_dev) (void)hipFree(h->tree_dev);
+    if (h->tree_pin) (void)hipHostFree(h->tree_pin);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     h->comm.destroy();
     if (h->st) (void)hipStreamDestroy(h->st);

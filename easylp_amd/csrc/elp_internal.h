@@ -475,4 +475,43 @@ struct ResItem {
 };
 hipError_t launch_resident_batch(const ResItem* items, int count, size_t lds, hipStream_t st);
 
+// resident branch and bound (k_resident_tree): run_bnb's loop
+// (elp_api.hip) around the node LP, inside the launch.  The tree record lives
+// in device memory: the header, the incumbent, and a stack of cap nodes (lo and
+// up of the n structurals in user units, as run_bnb keeps them).  failed holds a
+// public status code (include/easylp_hip.h ELP_*, mirrored below), -1: none.
+enum : int32_t { LPS_OPTIMAL = 0, LPS_SUBOPTIMAL = 1, LPS_INFEASIBLE = 2, LPS_UNBOUNDED = 3, LPS_NUMFAILURE = 5,
+                 LPS_TIMEOUT = 7 };
+// why a tree launch returned: the search is over (stack empty, unbounded, a
+// budget spent); the slice ran out between two nodes (launch again); the last
+// node failed numerically (the next starts cold: the host loop); a push would
+// overflow the stack (the popped node sits at slot sp, its x is the launch's
+// x: the host loop branches on it and goes on)
+enum : int32_t { TR_END = 0, TR_PAUSE = 1, TR_NODE_FAILED = 2, TR_STACK_FULL = 3 };
+struct TreeHdr {
+    int32_t cap, sp;  // stack capacity and nodes open
+    int32_t have, limit, unbounded, failed, reason;
+    int32_t warm_last;  // the node solved last was warm-started (elp_stats' reset)
+    int64_t nodes, iters, max_open;
+    int64_t launch_nodes;  // nodes solved by the last launch
+    int64_t max_nodes, max_iter;  // elp_control's (<= 0: none)
+    int64_t slice_nodes, slice_ticks;  // pause after so many nodes (> 0), else after so many ticks
+    double best;  // the incumbent's objective, minimising (+inf: none)
+    int64_t pad;
+};
+// obj: the user's objective; scol: the columns' scaling exponents (zeros when
+// unscaled); isint: elp_set_int's flags -- n each
+struct TreeArgs {
+    TreeHdr* hdr;
+    double* best_x;
+    const double* obj;
+    const int32_t* scol;
+    const int32_t* isint;
+    double* stack;  // node s: lo at [s * 2n], up at [s * 2n + n]
+};
+// as launch_resident, with a.ctl_out set; a.warm is ignored (the first node of
+// a fresh tree -- hdr->nodes == 0 -- starts from the load's state, every other
+// one warm)
+hipError_t launch_resident_tree(const Dev& d, const ResArgs& a, const TreeArgs& t, size_t lds, hipStream_t st);
+
 }  // namespace elp

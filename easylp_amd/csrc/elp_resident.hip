@@ -1393,8 +1393,17 @@ RDEV void r_gather(T* dst, int64_t cnt, F src) {
 // the LP's own: d's buffers, the workgroup's LDS (carved from d.m, d.n whatever
 // the launch allocated) and the per-workgroup r_stat / r_prof.
 // (BATCH: a.ctl_out is read; the single launch leaves the argument alone)
-template <bool BATCH>
-RDEV void r_solve(const Dev& d, const ResArgs& a) {
+//
+// TREE (k_resident_tree): the calling wave runs a whole depth-
+// first branch and bound -- elp_api.hip run_bnb's loop, statement for
+// statement -- around the node LP: the tree's nodes loop back into the one warm
+// block and the one main loop below (no second call site of any stage), the
+// LP state stays in LDS from node to node, and what the per-node path does
+// between two launches (reload_bounds_warm's control fields, the node's bounds
+// scaled, x unscaled, the objective, the branching column) happens here.  tp is
+// read only under TREE: the other two kernels compile to what they were.
+template <bool BATCH, bool TREE>
+RDEV void r_solve(const Dev& d, const ResArgs& a, const TreeArgs& tp) {
     extern __shared__ __attribute__((aligned(16))) char r_smem[];
     RS s;
     r_carve(s, r_smem, d.m, d.n);
@@ -1421,6 +1430,12 @@ RDEV void r_solve(const Dev& d, const ResArgs& a) {
         r_stat.iter_bytes = g->iter_bytes;
         r_stat.refactors = r_stat.gj = r_stat.resets = 0;
         r_stat.emax_max = 0.0;
+        if (TREE && tp.hdr->nodes > 0) {  // (a resumed tree: the last solved node's record stays its own)
+            r_stat.refactors = a.out->refactors;
+            r_stat.gj = a.out->gj_refactors;
+            r_stat.resets = a.out->devex_resets;
+            r_stat.emax_max = a.out->emax_max;
+        }
     }
     c.since = g->since_refactor;
     c.period = g->refactor_period;
@@ -1556,7 +1571,113 @@ RDEV void r_solve(const Dev& d, const ResArgs& a) {
     int recheck = 0, refac = RF_NONE;
     Piv P;
     int64_t flat = 0;
-    if (a.warm) {
+    bool warm = a.warm != 0;
+    // the tree (run_bnb's locals; uniform).  t_ran: a node LP ran in this
+    // launch, t_nwarm: how many of them warm
+    int t_sp = 0, t_have = 0, t_limit = 0, t_unb = 0, t_failed = -1, t_reason = TR_END, t_warm_last = 0;
+    int t_ran = 0, t_nwarm = 0;
+    int64_t t_nodes = 0, t_iters = 0, t_open = 0, t_lnodes = 0;
+    double t_best = R_INF;
+    if (TREE) {
+        const TreeHdr* th = tp.hdr;
+        t_sp = th->sp;
+        t_have = th->have;
+        t_limit = th->limit;
+        t_failed = th->failed;
+        t_warm_last = th->warm_last;
+        t_nodes = th->nodes;
+        t_iters = th->iters;
+        t_open = th->max_open;
+        t_best = th->best;
+    }
+node_next:
+    if (TREE) {
+        const TreeHdr* th = tp.hdr;
+        if (t_sp == 0) goto tree_done;  // (TR_END)
+        // the slice: the launch returns between two nodes, the host launches again
+        if (t_lnodes > 0 && (th->slice_nodes > 0 ? t_lnodes >= th->slice_nodes
+                                                 : (int64_t)(__builtin_amdgcn_s_memrealtime() - t0) > th->slice_ticks)) {
+            t_reason = TR_PAUSE;
+            goto tree_done;
+        }
+        --t_sp;  // pop: the node stays at slot t_sp until a push overwrites it
+        if (th->max_nodes > 0 && t_nodes >= th->max_nodes) {
+            t_limit = 1;
+            goto node_next;
+        }
+        if (a.tick_budget > 0 && (int64_t)(__builtin_amdgcn_s_memrealtime() - t0) > a.tick_budget) {
+            if (t_failed < 0) t_failed = LPS_TIMEOUT;
+            goto tree_done;
+        }
+        t_nodes++;
+        const int64_t left = th->max_iter > 0 ? th->max_iter - t_iters : (int64_t)100 * (m + n) + 10000;
+        if (th->max_iter > 0 && left <= 0) {  // budget spent: as the oracle
+            if (t_failed < 0) t_failed = LPS_SUBOPTIMAL;
+            goto tree_done;
+        }
+        c.iter_limit = left;
+        // the first node of a fresh tree runs from the load's state; every other
+        // one is reload_bounds_warm's: the node's bounds scaled (exact powers of
+        // two), the control block of a fresh solve with the basis kept
+        warm = t_nodes > 1;
+        if (warm) {
+            const double BIG = d.infinity;
+            const double *nlo = tp.stack + (size_t)t_sp * 2 * n, *nup = nlo + n;
+            bool bad = false;
+            for (int j = lane; j < n; j += RW) {
+                double l = nlo[j], u = nup[j];
+                const int e = tp.scol[j];
+                l = ldexp(l <= -BIG ? -R_INF : l >= BIG ? R_INF : l, -e);
+                u = ldexp(u <= -BIG ? -R_INF : u >= BIG ? R_INF : u, -e);
+                s.lb[j] = l;
+                s.ub[j] = u;
+                bad |= l > u;
+            }
+            R_FENCE();
+            c.status = ST_RUN;
+            c.phase = 3;
+            c.iter = 0;
+            c.since = 0;
+            c.ndegen = c.bland = 0;
+            c.devex = 0;
+            c.ddevex = a.price_rule == 1;
+            c.dv_valid = 0;
+            c.y_valid = 1;
+            recheck = 0;
+            refac = RF_NONE;
+            flat = 0;
+            if (lane == 0) {
+                r_stat.phase1_iters = r_stat.flips = r_stat.degenerate = r_stat.dual_iters = 0;
+                r_stat.unb_var = -1;
+                r_stat.price_bytes = r_stat.iter_bytes = 0.0;
+                r_stat.refactors = r_stat.gj = r_stat.resets = 0;
+                r_stat.emax_max = 0.0;
+                g->price_passes = 0;
+                g->plan.action = ACT_NONE;
+                g->plan_seq = g->applied_seq = g->copy_seq = 0;
+                g->infeasible_bounds = 0;
+            }
+            // the lanes past the bump and past Y as a load leaves them
+            if (lane >= c.ny) v.Yl = 0;
+            if (lane >= c.k) {
+                v.Rl = v.Sl = 0;
+                v.xs = 0.0;
+            }
+            v.acol = v.z = v.alU = v.alS = 0.0;
+            t_ran = 1;
+            t_nwarm++;
+            t_warm_last = 1;
+            if (__ballot(bad) != 0ull) {  // (the oracle's warm_core: nothing of the node runs)
+                c.status = ST_DUALINF;
+                t_lnodes++;
+                goto node_next;
+            }
+        } else {
+            t_ran = 1;
+            t_warm_last = 0;
+        }
+    }
+    if (warm) {
         // a branch-and-bound node from the last node's basis (reload_bounds_warm:
         // launch_warm_start, do_refactor, launch_devex_reset): the real costs, y
         // of them on the last inverse, each nonbasic column re-placed for the
@@ -1659,6 +1780,84 @@ RDEV void r_solve(const Dev& d, const ResArgs& a) {
         }
         c.since++;
     }
+    if (TREE) {
+        // the node is solved: run_bnb's statements after run_loop
+        R_FENCE();
+        t_lnodes++;
+        t_iters += c.iter;
+        const int st = c.status;
+        const int ls = st == ST_PHASE_OPT ? (c.phase == 1 ? LPS_INFEASIBLE : LPS_OPTIMAL)
+                       : st == ST_UNBOUNDED ? LPS_UNBOUNDED
+                       : st == ST_DUALINF   ? LPS_INFEASIBLE
+                       : st == ST_ITERCAP   ? LPS_SUBOPTIMAL
+                       : st == ST_TIMEOUT   ? LPS_TIMEOUT
+                                            : LPS_NUMFAILURE;
+        if (ls == LPS_UNBOUNDED) {
+            t_unb = 1;
+            goto tree_done;
+        }
+        if (ls != LPS_OPTIMAL && ls != LPS_INFEASIBLE) {  // limit or numerical failure
+            if (t_failed < 0) t_failed = ls;
+            // (a failed node leaves no basis to continue from: the next one starts
+            //  cold, which is the host's load)
+            if (ls == LPS_NUMFAILURE) t_reason = TR_NODE_FAILED;
+            goto tree_done;
+        }
+        if (ls != LPS_OPTIMAL) goto node_next;
+        // x as the exit forms it, unscaled (exact), into dvec; z = sum obj_j x_j by
+        // one sequential fma chain over j (elp_get_solution's); the lowest
+        // fractional integer column
+        double z = 0.0, xb = 0.0;
+        int jb = -1;
+        for (int j0 = 0; j0 < n; j0 += RW) {
+            const bool on = j0 + lane < n;
+            const int j = on ? j0 + lane : n - 1;
+            const int p = s.spos[j];
+            const double xbas = shf(v.xs, p & 63);
+            const double xu = ldexp(p >= 0 ? xbas : s.xval[j], tp.scol[j]);
+            const double oj = tp.obj[j];
+            if (on) s.dvec[j] = xu;
+            const int cnt = n - j0 < RW ? n - j0 : RW;
+            for (int l = 0; l < cnt; ++l) z = fma(rl(oj, l), rl(xu, l), z);
+            const unsigned long long fm = __ballot(on && tp.isint[j] != 0 && fabs(xu - rint(xu)) > 1e-7);
+            if (jb < 0 && fm != 0ull) {
+                const int fl = __ffsll((long long)fm) - 1;
+                jb = j0 + fl;
+                xb = rl(xu, fl);
+            }
+        }
+        R_FENCE();
+        const double zmin = d.maximize ? -z : z;
+        if (fabs(t_best) < R_INF) {
+            const double tol = fmax(1e-11, 1e-9 * fabs(t_best));
+            if (zmin >= t_best - tol) goto node_next;
+        }
+        if (jb < 0) {
+            t_best = zmin;
+            t_have = 1;
+            for (int j = lane; j < n; j += RW) tp.best_x[j] = s.dvec[j];
+            goto node_next;
+        }
+        if (t_sp + 2 > tp.hdr->cap) {  // (the host loop branches on this node's x and goes on)
+            t_reason = TR_STACK_FULL;
+            goto tree_done;
+        }
+        {
+            // floor child pushed first (in place of the node: only its upper bound
+            // changes), the ceiling child above it: explored first
+            double *flo = tp.stack + (size_t)t_sp * 2 * n, *fup = flo + n;
+            for (int j = lane; j < n; j += RW) {
+                const double l = flo[j], u = fup[j];
+                flo[2 * n + j] = j == jb ? ceil(xb) : l;
+                fup[2 * n + j] = u;
+                if (j == jb) fup[j] = floor(xb);
+            }
+            t_sp += 2;
+            if (t_sp > t_open) t_open = t_sp;
+        }
+        goto node_next;
+    }
+tree_done:
     R_FENCE();
     // ---- write back in the pipeline's layout
     const int k = c.k, ny = c.ny;
@@ -1737,7 +1936,13 @@ RDEV void r_solve(const Dev& d, const ResArgs& a) {
         g->flips = r_stat.flips;
         g->degenerate = r_stat.degenerate;
         g->dual_iters = r_stat.dual_iters;
-        if (a.warm) g->dflat += flat;
+        if (TREE) {  // (reload_bounds_warm zeroes dflat, sets the node's iteration limit and a new epoch)
+            if (t_ran && t_warm_last) g->dflat = flat;
+            if (t_ran) g->iter_limit = c.iter_limit;
+            g->mb_epoch += t_nwarm;
+        } else if (a.warm) {
+            g->dflat += flat;
+        }
         g->since_refactor = c.since;
         g->ndegen = c.ndegen;
         g->bland = c.bland;
@@ -1761,22 +1966,42 @@ RDEV void r_solve(const Dev& d, const ResArgs& a) {
         for (int i = 0; i < 8; ++i) a.out->stage[i] = ELP_RES_PROF ? (int64_t)(r_prof[i] + (i == 0 ? 0 : 0)) : 0;
         for (int i = 8; i < 16; ++i) a.out->stage2[i - 8] = ELP_RES_PROF ? (int64_t)r_prof[i] : 0;
         for (int i = 16; i < 24; ++i) a.out->stage3[i - 16] = ELP_RES_PROF ? (int64_t)r_prof[i] : 0;
-        if (BATCH && a.ctl_out) *a.ctl_out = *g;  // (the batch's arena: one copy back for every LP)
+        if ((BATCH || TREE) && a.ctl_out) *a.ctl_out = *g;  // (the batch's arena: one copy back for every LP)
+        if (TREE) {
+            TreeHdr* th = tp.hdr;
+            th->sp = t_sp;
+            th->have = t_have;
+            th->limit = t_limit;
+            th->unbounded = t_unb;
+            th->failed = t_failed;
+            th->reason = t_reason;
+            th->warm_last = t_warm_last;
+            th->nodes = t_nodes;
+            th->iters = t_iters;
+            th->max_open = t_open;
+            th->launch_nodes = t_lnodes;
+            th->best = t_best;
+        }
     }
 }
 
-__global__ void __launch_bounds__(RW) k_resident(Dev d, ResArgs a) { r_solve<false>(d, a); }
+__global__ void __launch_bounds__(RW) k_resident(Dev d, ResArgs a) { r_solve<false, false>(d, a, TreeArgs{}); }
 
 // Workgroup b solves items[b]: independent LPs side by side, each the single
 // launch's arithmetic.  The record's address is uniform and nothing the kernel
 // writes is const, so its fields are scalar loads as the kernel arguments are.
 __global__ void __launch_bounds__(RW) k_resident_batch(const ResItem* __restrict__ items) {
     const ResItem& it = items[blockIdx.x];
-    r_solve<true>(it.d, it.a);
+    r_solve<true, false>(it.d, it.a, TreeArgs{});
 }
 
+// One workgroup runs a small MIP's branch and bound: the node LPs, the stack
+// and the incumbent (the tree record t) without leaving the launch.  A batch
+// wrapper would call r_solve<true, true> per item the same way.
+__global__ void __launch_bounds__(RW) k_resident_tree(Dev d, ResArgs a, TreeArgs t) { r_solve<false, true>(d, a, t); }
+
 // hipFuncAttributeMaxDynamicSharedMemorySize as raised so far, per device and
-// kernel (which: 0 k_resident, 1 k_resident_batch)
+// kernel (which: 0 k_resident, 1 k_resident_batch, 2 k_resident_tree)
 hipError_t r_raise_lds(const void* fn, int which, size_t lds) {
     if (lds <= 65536) return hipSuccess;
     static std::mutex mu;
@@ -1806,6 +2031,13 @@ hipError_t launch_resident(const Dev& d, const ResArgs& a, size_t lds, hipStream
     const hipError_t e = r_raise_lds((const void*)k_resident, 0, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_resident, dim3(1), dim3(RW), lds, st, d, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_resident_tree(const Dev& d, const ResArgs& a, const TreeArgs& t, size_t lds, hipStream_t st) {
+    const hipError_t e = r_raise_lds((const void*)k_resident_tree, 2, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_resident_tree, dim3(1), dim3(RW), lds, st, d, a, t);
     return hipGetLastError();
 }
 

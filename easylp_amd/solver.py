@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import ElpStats, check, default_control, load
+from ._lib import ElpMipInfo, ElpStats, check, default_control, load
 
 # R/class.R:279-295
 STATUS_TEXT = {
@@ -66,6 +66,7 @@ class Solution:
     stats: dict = field(default_factory=dict)
     trace: np.ndarray | None = None
     sens: dict | None = None      # sensitivity report (Problem.sensitivity)
+    mip: dict | None = None       # how the branch and bound ran (Problem.mip_info), None for an LP
 
     @property
     def status_text(self) -> str:
@@ -207,6 +208,15 @@ class Problem:
         check(self._lib.elp_get_stats(self._h, ctypes.byref(s)), "elp_get_stats")
         return {f: getattr(s, f) for f, _ in ElpStats._fields_}
 
+    def mip_info(self) -> dict | None:
+        """elp_get_mip_info of the last solve: nodes, lp_iterations, tree_launches
+        (launches of the resident tree kernel; 0: the per-node host loop),
+        tree_nodes, handbacks, max_open.  None when the last solve was no MIP."""
+        info = ElpMipInfo()
+        if self._lib.elp_get_mip_info(self._h, ctypes.byref(info)) != 0:
+            return None
+        return {f: getattr(info, f) for f, _ in ElpMipInfo._fields_ if f != "reserved"}
+
     def trace(self) -> np.ndarray:
         cap = self._trace_cap
         buf = np.zeros(2 * max(cap, 1), dtype=np.int64)
@@ -235,7 +245,7 @@ class Problem:
         check(self._lib.elp_get_solution(self._h, ctypes.byref(obj), x.ctypes.data,
                                          y.ctypes.data, basis.ctypes.data), "elp_get_solution")
         tr = self.trace() if self._trace_cap else None
-        return Solution(status, obj.value, x, y[:m], basis[:m], self.stats(), tr)
+        return Solution(status, obj.value, x, y[:m], basis[:m], self.stats(), tr, mip=self.mip_info())
 
 
 def generate_dense_device(seed: int, m: int, n: int, device: int = 0):

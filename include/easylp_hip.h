@@ -137,8 +137,11 @@ typedef struct elp_control {
                                 fits (one GPU, no column shards); 1: the same
                                 (force: the tests); 2: never (the multi-workgroup
                                 pipeline).  Same pivots, same bits either way;
-                                branch-and-bound nodes warm-start inside the
-                                same launch; elp_stats.resident reports what ran */
+                                a MIP's whole branch and bound -- every node's
+                                warm start and LP, the node stack, the
+                                incumbent -- runs inside launches of the same
+                                wave (elp_get_mip_info);
+                                elp_stats.resident reports what ran */
     int32_t pad_resident;
 } elp_control;
 
@@ -195,7 +198,9 @@ typedef struct elp_stats {
     double seconds_h2d;        /* elp_load_dense: host -> device copy of A     */
     double h2d_bytes;          /* bytes of A read from host memory (once, also
                                   when several devices receive them)            */
-    int64_t resident_launches; /* resident-solver launches of the last solve     */
+    int64_t resident_launches; /* resident-solver launches of the last solve
+                                  (a MIP: of its resident tree, elp_mip_info.
+                                  tree_launches; of the last node on the host loop) */
     int64_t resident_ticks;    /* their device time (s_memrealtime, 100 MHz)   */
     int32_t basis;             /* the representation the last load used
                                   (ELP_BASIS_INVERSE)                           */
@@ -279,7 +284,9 @@ int elp_generate_dense(int32_t device, uint64_t seed, int64_t m, int64_t n, doub
  * NULL clears.  Call after elp_load_*, before elp_solve, which then runs a
  * depth-first branch and bound over GPU LP relaxations (lowest-index
  * fractional column, ceiling branch first, as lp_solve's defaults) and reports
- * the incumbent through elp_get_solution. */
+ * the incumbent through elp_get_solution.  A MIP the resident solver takes
+ * (elp_control.resident, SIMPLEX_DUAL_PRIMAL) runs the whole tree on the device
+ * (elp_get_mip_info); any other pays one host round trip per node. */
 int elp_set_int(elp_handle* h, const int32_t* is_int);
 
 /* solve(prob)                                          R/class.R:276 */
@@ -319,6 +326,24 @@ int elp_iterate(elp_handle* h, int64_t iters, int32_t* lp_status);
 int elp_get_solution(elp_handle* h, double* objval, double* x, double* y, int64_t* basis);
 
 int elp_get_stats(elp_handle* h, elp_stats* st);
+
+/* How the last elp_solve's branch and bound ran (elp_set_int).  A MIP the
+ * resident solver takes (elp_control.resident: m <= 64, the state fits in LDS,
+ * one GPU, SIMPLEX_DUAL_PRIMAL) runs its whole tree inside launches of one
+ * wave: node LPs, node stack and incumbent stay on the device, a launch
+ * returns after ~20 ms to be launched again (tree_launches counts them), and
+ * the rest of a search goes back to the per-node host loop when a node fails
+ * numerically or more nodes are open than the device stack holds (256).
+ * Same tree, same bits either way. */
+typedef struct elp_mip_info {
+    int64_t nodes, lp_iterations;   /* = elp_stats.mip_nodes / mip_lp_iterations */
+    int64_t tree_launches;          /* launches of the resident tree kernel (0: host loop) */
+    int64_t tree_nodes;             /* nodes counted inside them */
+    int64_t handbacks;              /* times the rest of the search went back to the host loop */
+    int64_t max_open;               /* most nodes open on the stack at once */
+    int64_t reserved[2];
+} elp_mip_info;
+int elp_get_mip_info(elp_handle* h, elp_mip_info* info);  /* ELP_E_STATE: the last solve was no MIP */
 
 /* get.sensitivity.obj / get.sensitivity.rhs             R/class.R:613-646
  * Sensitivity report of the final basis of an OPTIMAL solve (ELP_E_STATE
